@@ -1,7 +1,16 @@
 """bench.py — Gkeys/s of the MI355X radix sort (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3|c5|ns] [--dist uniform|perm]
+                  [--dump-outputs DIR] [--full]
   (N > 1: torchrun --nproc-per-node N ... bench.py --gpus N ...; one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's output under
+--dump-outputs (if given) and prints the result line with the headline figure: `value`,
+`ms_per_step` (wall milliseconds per timed step), the workload and the whole-sort roofline
+arithmetic.  Everything that takes runs of its own (the per-phase hipEvent re-run behind
+`roofline` / `moved_roofline` / `phases_ms`, the rocprofv3 PMC child runs, the CPU baseline, the
+north-star and reference-input legs) runs only with --full; what is said about those below
+describes a --full run.
 
 A step = one complete sort of one batch of synthetic keys already resident in HBM
 (key[i] = splitmix64(seed ^ global_i)).  Every step sorts its OWN unsorted
@@ -16,11 +25,11 @@ the presorted exchange (local sort, bit-packed delta encoding of the buckets, on
 recv per peer over xGMI, decode, merge), beyond that the partition-first one (range partition,
 one RCCL all-to-all, local sort).  `value` = 2^30 keys x steps / wall time.
 
-At N = 1 the default line also carries `north_star` (2^28 uniform u32 keys, BASELINE's
+With --full, at N = 1 the default line also carries `north_star` (2^28 uniform u32 keys, BASELINE's
 north-star target) and `reference_input` (the reference's own input, 0..N-1 shuffled,
 main.cpp:119-125, at 2^28 and 2^30: the MSD digits adapt to its 28 / 30-bit span).
 
-Rank 0 prints ONE JSON line with the driver contract plus:
+Rank 0 prints ONE JSON line with the driver contract plus, with --full:
   roofline      dominant kernel (the LSD schedule's pass: grs_onesweep_v4, or v6 on small
                 grids; the MSD schedule's slowest of its two scatters and its LDS sort, each of
                 which reads and writes every key once): algorithmic bytes per launch
@@ -102,7 +111,19 @@ def parse():
     ap.add_argument("--pool-gib", type=float, default=160.0,
                     help="HBM budget for the distinct per-step input buffers (the default holds "
                          "warmup + steps C4 inputs of 4 GiB at the default 3 + 20 and 5 + 20)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step's sort returned "
+                         "(this rank's sorted keys, and the payload of a pair config) as "
+                         "DIR/<name>.npy in float64; an output of more than DUMP_SAMPLE elements "
+                         "is written as a fixed sample of its positions (dump_sample_index)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-phase hipEvent "
+                         "re-run (roofline, moved_roofline, phases_ms), the rocprofv3 PMC child "
+                         "runs, the CPU baseline, the north-star and reference-input legs")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def usable_cores():
@@ -167,6 +188,59 @@ def config_seed(cid):
     as oracle.config_seed, restated: bench.py's timed legs do not import the oracle)."""
     s = 0x6A09E667F3BCC908 + cid + ((1 << 48) if cid == 6 else 0)
     return s & ((1 << 64) - 1)
+
+
+DUMP_SAMPLE = 1 << 21   # elements per dumped array: 16 MiB in float64, at most 3 arrays per rank
+DUMP_SEED = 0x243F6A8885A308D3
+
+
+def dump_sample_index(n):
+    """Positions of an n-element output that --dump-outputs writes: every one up to DUMP_SAMPLE
+    elements; beyond, one position in each of DUMP_SAMPLE equal strata, picked by
+    splitmix64(DUMP_SEED + stratum), with the first and the last element always among them.
+    A function of n alone, so two builds write the same positions."""
+    import numpy as np
+
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    j = np.arange(DUMP_SAMPLE, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = j + np.uint64(DUMP_SEED) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    lo = j * np.uint64(n) // np.uint64(DUMP_SAMPLE)          # n < 2^42: no overflow
+    hi = (j + np.uint64(1)) * np.uint64(n) // np.uint64(DUMP_SAMPLE)
+    idx = (lo + z % (hi - lo)).astype(np.int64)
+    idx[0], idx[-1] = 0, n - 1
+    return idx
+
+
+def dump_outputs(dirname, rank, world, keys, vals):
+    """Write the sorted keys (and payload) a caller of the timed sort received, float64 .npy:
+    u32 values are exact in float64; u64 keys go out as their high and low 32-bit halves."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    idx = torch.from_numpy(dump_sample_index(keys.numel())).to(keys.device)
+
+    def take(t):   # torch indexes the signed dtypes; the bits are the same
+        wide = t.element_size() == 8
+        s = t.view(torch.int64 if wide else torch.int32)[idx].cpu().numpy()
+        return s.view(np.uint64 if wide else np.uint32)
+
+    def save(name, arr):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), arr.astype(np.float64))
+
+    k = take(keys)
+    if k.dtype == np.uint64:
+        save("keys_hi32", k >> np.uint64(32))
+        save("keys_lo32", k & np.uint64(0xFFFFFFFF))
+    else:
+        save("keys", k)
+    if vals is not None:
+        save("vals", take(vals))
 
 
 def pmc_probe(a, options):
@@ -293,9 +367,10 @@ def moved_bytes(n, kb, pairs, rb, schedule):
 
 
 def run_config(a, config, world, rank, local, dev, sharded, steps, warmup, dist="uniform",
-               traffic=True, cpu=True):
+               traffic=True, cpu=True, full=True, dump=""):
     """One workload of CONFIGS, timed per the driver contract; returns rank 0's JSON dict.
-    dist: "uniform" (splitmix64) or "perm" (the reference's shuffled 0..N-1)."""
+    dist: "uniform" (splitmix64) or "perm" (the reference's shuffled 0..N-1).  full=False ends
+    after the timed steps (and the dump): no per-phase re-run, PMC child runs or CPU baseline."""
     import gpuradixsort_amd as grs
 
     cid, n_cfg, kb, pairs, rb, desc = CONFIGS[config]
@@ -379,6 +454,41 @@ def run_config(a, config, world, rank, local, dev, sharded, steps, warmup, dist=
     # correctness of the last timed step (cheap property: sortedness on device)
     last = (warmup + steps - 1) % pool
     inversions = sorter.count_inversions() if sharded else grs.count_inversions(keys_pool[last])
+    if dump:
+        if sharded:
+            m = sorter.last_n_out
+            dump_outputs(dump, rank, world, sorter.out_k[:m], sorter.out_v[:m] if pairs else None)
+        else:
+            dump_outputs(dump, rank, world, keys_pool[last], vals_pool[last] if pairs else None)
+
+    # SURVEY §8d credits P_cfg = key bits / digit bits passes, whatever schedule ran
+    passes = kb // rb
+    sort_alg = n_local * 2 * passes * (kb // 8 + (4 if pairs else 0))
+    head = {
+        "metric": METRIC, "value": round(n_total * steps / elapsed / 1e9, 3), "unit": "Gkeys/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(elapsed / steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u32" if kb == 32 else "u64",
+        "data": ("synthetic: splitmix64(seed ^ global_index) uniform keys" if dist == "uniform" else
+                 "synthetic: the reference's input, 0..N-1 shuffled by a seeded bijection "
+                 "(grs_fill_permutation; main.cpp:119-125)")
+                + ", a distinct unsorted buffer per step resident in HBM"
+                + ("; payload = global index" if pairs else ""),
+        "config": {"workload": desc, "dist": dist, "keys_per_gpu": n_local, "total_keys": n_total,
+                   "key_bits": kb, "payload": "u32" if pairs else None, "radix_bits": rb,
+                   "passes": passes, "parallelism": f"range-shard x{world}"},
+        # whole-sort view of SURVEY.md §8d: B_alg = N x 2 x passes x (key + value bytes)
+        # over the whole step (histogram and exchange included)
+        "sort_roofline": {"achieved": round(sort_alg / (elapsed / steps) / 1e9, 1),
+                          "frac": round(sort_alg / (elapsed / steps) / 1e9 / HBM_PEAK_GBPS, 4),
+                          "alg_bytes_per_step": sort_alg, "unit": "GB/s",
+                          "credited_passes": passes},
+        "check": {"inversions_last_step": inversions},
+    }
+    if options:
+        head["config"]["options"] = options
+    if not full:
+        return head if rank == 0 else None
 
     # per-phase GPU times: the same steps again, untimed, with libgrs's per-phase hipEvent ring
     # on (events between the launches cost 2-5 us each, 13 % of a C2 sort; the timed steps above
@@ -431,8 +541,6 @@ def run_config(a, config, world, rank, local, dev, sharded, steps, warmup, dist=
                        "p3_local_sort": "grs_msd_local"}[dom]
     alg_bytes = n_sorted_local * 2 * (kb // 8 + (4 if pairs else 0)) * (kb // rb if fused else 1)
     achieved = alg_bytes / (mean_pass_ms * 1e-3) / 1e9
-    # SURVEY §8d credits P_cfg = key bits / digit bits passes, whatever schedule ran
-    passes = kb // rb
     del keys_pool, vals_pool, sorter
     torch.cuda.empty_cache()
 
@@ -454,37 +562,18 @@ def run_config(a, config, world, rank, local, dev, sharded, steps, warmup, dist=
         if rec.get("n") == n_sorted_local and rec.get("config") == config:
             traffic = rec.get("hbm_bytes_per_launch")
 
-    sort_alg = n_local * 2 * passes * (kb // 8 + (4 if pairs else 0))
     schedule = "msd" if msd else "lsd-fused" if fused else "lsd"
     moved = moved_bytes(n_sorted_local, kb, pairs, rb, "msd" if msd else "lsd")
     if rank != 0:
         return None
-    value = n_total * steps / elapsed / 1e9
     out = {
-        "metric": METRIC, "value": round(value, 3), "unit": "Gkeys/s", "n_gpus": world,
-        "steps": steps, "warmup": warmup,
-        "ms_per_step": round(elapsed / steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u32" if kb == 32 else "u64",
-        "data": ("synthetic: splitmix64(seed ^ global_index) uniform keys" if dist == "uniform" else
-                 "synthetic: the reference's input, 0..N-1 shuffled by a seeded bijection "
-                 "(grs_fill_permutation; main.cpp:119-125)")
-                + ", a distinct unsorted buffer per step resident in HBM"
-                + ("; payload = global index" if pairs else ""),
-        "config": {"workload": desc, "dist": dist, "keys_per_gpu": n_local, "total_keys": n_total,
-                   "key_bits": kb, "payload": "u32" if pairs else None, "radix_bits": rb,
-                   "passes": passes, "parallelism": f"range-shard x{world}"},
+        **head,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                      "traffic": traffic, "kernel": kernel_name,
                      "kernel_mean_ms": round(mean_pass_ms, 5),
                      "alg_bytes_per_launch": alg_bytes,
                      "traffic_over_alg": round(traffic / alg_bytes, 4) if traffic else None},
-        # whole-sort view of SURVEY.md §8d: B_alg = N x 2 x passes x (key + value bytes)
-        # over the whole step (histogram and exchange included)
-        "sort_roofline": {"achieved": round(sort_alg / (elapsed / steps) / 1e9, 1),
-                          "frac": round(sort_alg / (elapsed / steps) / 1e9 / HBM_PEAK_GBPS, 4),
-                          "alg_bytes_per_step": sort_alg, "unit": "GB/s",
-                          "credited_passes": passes},
         # what the schedule that ran actually moves (moved_bytes), over the same step time
         "moved_roofline": {"bytes_per_step": moved,
                            "achieved": round(moved / (elapsed / steps) / 1e9, 1),
@@ -544,10 +633,12 @@ def main():
             port = so.getsockname()[1]
         dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
 
-    out = run_config(a, a.config, world, rank, local, dev, sharded, a.steps, a.warmup, a.dist)
+    out = run_config(a, a.config, world, rank, local, dev, sharded, a.steps, a.warmup, a.dist,
+                     full=a.full, dump=a.dump_outputs)
     keep = ("value", "unit", "ms_per_step", "steps", "warmup", "roofline", "sort_roofline",
             "moved_roofline", "phases_ms", "check", "schedule", "config", "traffic_pmc")
-    default_line = world == 1 and not sharded and a.config == "c4" and not a.n and a.dist == "uniform"
+    default_line = (a.full and world == 1 and not sharded and a.config == "c4" and not a.n
+                    and a.dist == "uniform")
     # the north star's own 1-GPU target (BASELINE.json: >= 60 % of the HBM roofline on 256 M
     # uniform uint32 keys) as a second leg of the same driver-timed run, after the headline
     if default_line and not a.no_north_star:

@@ -39,6 +39,43 @@ def test_parse_defaults(monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.config, a.dist, a.n) == (1, "c4", "uniform", 0)
     assert 1 <= a.steps <= 100 and 0 <= a.warmup <= 10
+    # a plain run: the headline only, nothing written
+    assert a.full is False and a.dump_outputs == ""
+
+
+def test_parse_full_dump_and_steps(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "0",
+                                      "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 0, True, "out")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_sample_index():
+    import numpy as np
+
+    # up to DUMP_SAMPLE elements: every position
+    assert np.array_equal(bench.dump_sample_index(5), np.arange(5))
+    assert np.array_equal(bench.dump_sample_index(bench.DUMP_SAMPLE), np.arange(bench.DUMP_SAMPLE))
+    # three float64 arrays per rank (u64 key halves + payload) stay within 64 MB
+    assert 3 * bench.DUMP_SAMPLE * 8 <= 64 * 10**6
+    for n in (bench.DUMP_SAMPLE + 1, 3 * bench.DUMP_SAMPLE + 17, 1 << 30, (1 << 32) - (1 << 16)):
+        idx = bench.dump_sample_index(n)
+        assert idx.dtype == np.int64 and idx.shape == (bench.DUMP_SAMPLE,)
+        assert idx[0] == 0 and idx[-1] == n - 1
+        assert np.all(np.diff(idx) >= 0) and idx.max() < n
+        # one position per stratum [j n / S, (j + 1) n / S)
+        j = np.arange(bench.DUMP_SAMPLE, dtype=np.uint64)
+        lo = (j * np.uint64(n) // np.uint64(bench.DUMP_SAMPLE)).astype(np.int64)
+        hi = ((j + np.uint64(1)) * np.uint64(n) // np.uint64(bench.DUMP_SAMPLE)).astype(np.int64)
+        assert np.all(idx >= lo) and np.all(idx < hi)
+        # a function of n alone
+        assert np.array_equal(idx, bench.dump_sample_index(n))
+    # jittered, not a fixed stride: the offsets within the strata vary
+    idx = bench.dump_sample_index(1 << 30)
+    assert len(np.unique(idx[1:-1] % 512)) > 256
 
 
 @pytest.mark.parametrize("n,kb,pairs,want", [

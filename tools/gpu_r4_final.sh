@@ -20,11 +20,11 @@ run() {
 if [[ $PART == *a* ]]; then
   run pytest 600 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread -p no:cacheprovider || exit $?
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-  run bench 500 python -u bench.py || exit $?
+  run bench 500 python -u bench.py --full || exit $?
   run extras 300 python -u tools/bench_extras.py || exit $?
 fi
 if [[ $PART == *b* ]]; then
-  for c in c2 c3 c5; do run bench_$c 300 python -u bench.py --config $c --steps 10 --no-cpu-baseline || exit $?; done
+  for c in c2 c3 c5; do run bench_$c 300 python -u bench.py --full --config $c --steps 10 --no-cpu-baseline || exit $?; done
   run prof_c4 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof_c4 -o run --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-traffic --no-north-star || exit $?
   run prof_ns 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof_ns -o run --output-format csv -- python3 bench.py --config ns --steps 10 --warmup 2 --no-cpu-baseline --no-traffic || exit $?
   run prof_c2 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof_c2 -o run --output-format csv -- python3 bench.py --config c2 --steps 10 --warmup 2 --no-cpu-baseline --no-traffic || exit $?
