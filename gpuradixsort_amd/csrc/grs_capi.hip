@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -317,6 +318,7 @@ struct grs_sorter {
   int fault_tile = -1;             // GRS_OPT_FAULT_TILE (test hook; ctrl debug words)
   uint32_t h2_chunk = 0;           // GRS_OPT_H2_CHUNK: 0 by size, else H2's chunk (keys per block)
   uint32_t h2_piece = 0;           // GRS_OPT_H2_PIECE: 0 default, else H2's sample piece (keys)
+  int p3_shape = 0;                // GRS_OPT_P3_SHAPE (test hook): 0 by size, else a msd_local_shape code
   int p3_mode = 0;                 // GRS_OPT_P3: 0 a workgroup per segment, 1 persistent with
                                    // prefetch (u32 keys / pairs; measured slower, round 6), 2 as 0
                                    // without the low-halves kernel for C4's size
@@ -508,6 +510,32 @@ using MsdLocalC = MsdLocal<768, 24, true>;    // 4-byte elements: two 72-KB work
 using MsdLocalD = MsdLocal<1024, 36, true>;   // 4-byte elements past 1.13G keys: one 152-KB workgroup
                                               // per CU (the MSD sort to ~2.3G keys)
 constexpr uint32_t kMsdSmaxMin = MsdLocalS::SMAX;
+// The P3 shape type of a msd_local_shape code for keys K (+ payload), handed to f as a value;
+// false when that shape has no run_msd instantiation for the type (C2 / C / D: u32 keys only).
+// The sort's launch, GRS_OPT_P3_SHAPE's range check and grs_debug_p3_kernel all map codes here.
+template <typename K, bool PAIRS, typename F>
+bool with_msd_shape(int code, F&& f) {
+  constexpr bool kKeys32 = sizeof(K) == 4 && !PAIRS;
+  switch (code) {
+    case 4: f(MsdLocalS{}); return true;
+    case 5: f(MsdLocalM{}); return true;
+    case 1:
+      if constexpr (sizeof(K) == 8) f(MsdLocalW{});
+      else f(MsdLocalA{});
+      return true;
+    case 2: f(MsdLocalB{}); return true;
+    case 7:
+      if constexpr (kKeys32) f(MsdLocalC2{});
+      return kKeys32;
+    case 3:
+      if constexpr (kKeys32) f(MsdLocalC{});
+      return kKeys32;
+    case 6:
+      if constexpr (kKeys32) f(MsdLocalD{});
+      return kKeys32;
+    default: return false;
+  }
+}
 // fallback and redo passes (persistent): the big tile of the key type; 17408 keys is the
 // smallest of them (u32 pairs, u64 keys), which sizes the tables
 constexpr uint32_t kMsdTileMin = 17408;
@@ -776,7 +804,16 @@ grs_status grs_set_option(grs_sorter* s, grs_option opt, int value) {
       if (value < 0 || value > 2) return bad();
       s->p3_mode = value;
       break;
-
+    case GRS_OPT_P3_SHAPE: {
+      const auto none = [](auto) {};
+      const bool ok = value == 0 || (s->key_type == GRS_KEY_U32
+                                         ? (s->pairs ? with_msd_shape<uint32_t, true>(value, none)
+                                                     : with_msd_shape<uint32_t, false>(value, none))
+                                         : !s->pairs && with_msd_shape<uint64_t, false>(value, none));
+      if (!ok) return bad();
+      s->p3_shape = value;
+      break;
+    }
     default:
       return set_err(GRS_EINVAL, "grs_set_option: unknown option");
   }
@@ -821,6 +858,7 @@ grs_status grs_get_option(const grs_sorter* s, grs_option opt, int* value) {
     case GRS_OPT_H2_CHUNK: *value = static_cast<int>(s->h2_chunk); break;
     case GRS_OPT_H2_PIECE: *value = static_cast<int>(s->h2_piece); break;
     case GRS_OPT_P3: *value = s->p3_mode; break;
+    case GRS_OPT_P3_SHAPE: *value = s->p3_shape; break;
     default: return set_err(GRS_EINVAL, "grs_get_option: unknown option");
   }
   return GRS_OK;
@@ -1239,6 +1277,54 @@ int msd_local_shape(size_t n, size_t elem) {
   return 0;
 }
 
+// The P3 kernel of one sort: what run_msd launches and what grs_debug_p3_kernel names.
+struct MsdP3Kernel {
+  enum Family { kLocal, kLocalPf, kLocal16 } family;
+  int block, items;    // the instantiation's <BLOCK, I> (kLocal16: of the low-halves sort)
+  uint32_t smax;       // keys of the longest segment it sorts itself
+  uint32_t mid_max;    // longer segments up to this many keys: the mid list; past it: the fallback
+  bool list;           // grs_msd_local_list (the larger shape) follows; else grs_msd_copy_big
+};
+// P3L: the mid list's shape for the type.  p3_mode: GRS_OPT_P3.
+template <typename K, bool PAIRS, typename P3C>
+MsdP3Kernel msd_p3_kernel(size_t n, int p3_mode) {
+  using P3L = std::conditional_t<sizeof(K) == 4 && !PAIRS, MsdLocalC, MsdLocalB>;
+  const uint32_t mid_max = P3L::SMAX > P3C::SMAX ? P3L::SMAX : P3C::SMAX;
+  const bool list = P3L::SMAX > P3C::SMAX;
+  const MsdP3Kernel whole{MsdP3Kernel::kLocal, P3C::BLOCK, P3C::I, P3C::SMAX, mid_max, list};
+  if constexpr (sizeof(K) == 4) {
+    if (p3_mode == 1) return {MsdP3Kernel::kLocalPf, P3C::BLOCK, P3C::I, P3C::SMAX, mid_max, list};
+    if constexpr (!PAIRS && P3C::SMAX == MsdLocalC2::SMAX) {
+      // C4's 2^30 keys: the low halves in LDS, three workgroups a CU (grs_msd_local16; tools/lab8.py
+      // round 6: 1.90 vs 1.96 ms uniform, 1.83 vs 1.99 on the reference's input).  Segments past
+      // its 17408 keys (8 sigma above the mean at 2^30) take the mid list
+      if (p3_mode == 0) return {MsdP3Kernel::kLocal16, 512, 34, 512u * 34u, mid_max, list};
+    }
+    if constexpr (!PAIRS && P3C::SMAX == MsdLocalD::SMAX) {
+      // past 1.13G keys up to ~2.18G: 1024 x 34 low halves, two workgroups a CU where LocalSort's
+      // 1024 x 36 fits one (lab at 2^31: 4.81 vs ~5.3 ms).  No mid list in this shape's sort: a
+      // segment past 34816 keys takes the fallback
+      if (p3_mode == 0 && msd_segment_need(n) <= 1024 * 34)
+        return {MsdP3Kernel::kLocal16, 1024, 34, 1024u * 34u, 1024u * 34u, list};
+    }
+  }
+  return whole;
+}
+
+// "family<BLOCK,I>" of a P3 kernel (grs_debug_p3_kernel); interned, so the pointer stays valid.
+const char* msd_p3_kernel_name(const MsdP3Kernel& k) {
+  static const char* const family[] = {"grs_msd_local", "grs_msd_local_pf", "grs_msd_local16"};
+  static std::mutex mu;
+  static std::set<std::string> names;
+  const std::string name =
+      std::string(family[k.family]) + "<" + std::to_string(k.block) + "," + std::to_string(k.items) + ">";
+  std::lock_guard<std::mutex> lock(mu);
+  return names.insert(name).first->c_str();
+}
+
+// The P3 shape code of a sort of n elements of `elem` bytes: GRS_OPT_P3_SHAPE's pin, else by size.
+int msd_shape_code(int pinned, size_t n, size_t elem) { return pinned != 0 ? pinned : msd_local_shape(n, elem); }
+
 bool use_msd(const grs_sorter* s, size_t n, int begin_bit, int end_bit) {
   if (!msd_type(s) || s->msd_mode == 0 || s->msd_buf == nullptr || s->rank_mode != 0) return false;
   const int kbits = s->key_type == GRS_KEY_U64 ? 64 : 32;
@@ -1397,7 +1483,7 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
   // exact counts, persistent scatter); otherwise the two launches leave at once
   hipLaunchKernelGGL((grs::grs_msd_span<K, FT::TILE>), dim3(1), dim3(256), 0, stream, n, span, totals, recf, hdrf);
   GRS_HIP(hipGetLastError());
-  hipLaunchKernelGGL((grs::grs_seg_hist<K, 1>), dim3(2 * s->cus), dim3(256), 0, stream, src, recf, hdrf,
+  hipLaunchKernelGGL((grs::grs_seg_hist<K, 1, true>), dim3(2 * s->cus), dim3(256), 0, stream, src, recf, hdrf,
                      0, exact, st[0], 256u, top);
   GRS_HIP(hipGetLastError());
   hipLaunchKernelGGL((grs::grs_onesweep_seg<K, PAIRS, 8, FT::BLOCK, FT::ITEMS, FT::MINW, FT::OPT, true>),
@@ -1510,9 +1596,11 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
   // range after the multi-GPU exchange), beyond that for the fallback (moved to their place
   // first: grs_msd_copy_big)
   using P3L = std::conditional_t<sizeof(K) == 4 && !PAIRS, MsdLocalC, MsdLocalB>;
-  const uint32_t mid_max = P3L::SMAX > P3C::SMAX ? P3L::SMAX : P3C::SMAX;
+  const MsdP3Kernel pk = msd_p3_kernel<K, PAIRS, P3C>(n, s->p3_mode);   // (grs_debug_p3_kernel names it)
+  const uint32_t mid_max = pk.mid_max;
+  bool launched = false;
   if constexpr (sizeof(K) == 4) {
-    if (s->p3_mode == 1) {
+    if (pk.family == MsdP3Kernel::kLocalPf) {
       // persistent, the next segment's loads behind this one's stores (grs_msd_local_pf; the
       // ticket: big[16], zeroed by the sample kernel).  Measured slower than a workgroup per
       // segment (C4 P3 2.12 vs 1.97 ms, ns 0.80 vs 0.45: the ticket and the segment's table
@@ -1527,33 +1615,27 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
                          dim3(per_cu * std::max(1, s->cus)), dim3(P3C::BLOCK), 0, stream, keys, vals, rk, rv, spill2,
                          mb + L.len2, mb + L.in2, mb + L.out2, mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart,
                          mb + L.blen, mb + L.brow, rows, top, bigc + 16);
-    } else if (!PAIRS && P3C::SMAX == MsdLocalC2::SMAX && s->p3_mode == 0) {
-      // C4's 2^30 keys: the low halves in LDS, three workgroups a CU (grs_msd_local16; tools/lab8.py
-      // round 6: 1.90 vs 1.96 ms uniform, 1.83 vs 1.99 on the reference's input).  Segments past
-      // its 17408 keys (8 sigma above the mean at 2^30) take the mid list
+      launched = true;
+    } else if (pk.family == MsdP3Kernel::kLocal16 && pk.block == 512) {
       hipLaunchKernelGGL((grs::grs_msd_local16<512, 34, 6, FT::TILE>), dim3(65536), dim3(512), 0, stream,
                          (uint32_t*)keys, vals, (const uint32_t*)rk, rv, spill2, mb + L.len2, mb + L.in2, mb + L.out2,
                          mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top);
-    } else if (!PAIRS && P3C::SMAX == MsdLocalD::SMAX && s->p3_mode == 0 && msd_segment_need(n) <= 1024 * 34) {
-      // past 1.13G keys up to ~2.18G: 1024 x 34 low halves, two workgroups a CU where LocalSort's
-      // 1024 x 36 fits one (lab at 2^31: 4.81 vs ~5.3 ms).  No mid list in this shape's sort: a
-      // segment past 34816 keys takes the fallback
+      launched = true;
+    } else if (pk.family == MsdP3Kernel::kLocal16) {
       hipLaunchKernelGGL((grs::grs_msd_local16<1024, 34, 8, FT::TILE>), dim3(65536), dim3(1024), 0, stream,
                          (uint32_t*)keys, vals, (const uint32_t*)rk, rv, spill2, mb + L.len2, mb + L.in2, mb + L.out2,
-                         1024u * 34u, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top);
-    } else {
-      hipLaunchKernelGGL((grs::grs_msd_local<K, PAIRS, P3C::BLOCK, P3C::I, P3C::C16, FT::TILE>), dim3(65536),
-                         dim3(P3C::BLOCK), 0, stream, keys, vals, rk, rv, spill2, mb + L.len2, mb + L.in2,
-                         mb + L.out2, mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow,
-                         rows, top);
+                         mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top);
+      launched = true;
     }
-  } else {
+  }
+  if (!launched) {
+    if (pk.family != MsdP3Kernel::kLocal) return set_err(GRS_EINVAL, "internal: no P3 kernel of that family for this type");
     hipLaunchKernelGGL((grs::grs_msd_local<K, PAIRS, P3C::BLOCK, P3C::I, P3C::C16, FT::TILE>), dim3(65536),
                        dim3(P3C::BLOCK), 0, stream, keys, vals, rk, rv, spill2, mb + L.len2, mb + L.in2, mb + L.out2,
                        mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top);
   }
   GRS_HIP(hipGetLastError());
-  if (P3L::SMAX > P3C::SMAX) {
+  if (pk.list) {
     constexpr int per_cu = P3L::SMAX * (sizeof(K) + (PAIRS ? 4 : 0)) <= 80 * 1024 ? 2 : 1;
     constexpr int minw = per_cu * P3L::BLOCK / GRS_WAVE / 4;
     // (with grs_msd_copy_big's work: one launch fewer)
@@ -1603,24 +1685,12 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
 template <typename K, bool PAIRS>
 grs_status run_sort_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream_t stream,
                         const K* src_in = nullptr, const uint32_t* vsrc_in = nullptr) {
-  switch (msd_local_shape(n, sizeof(K) + (PAIRS ? 4 : 0))) {
-    case 4: return run_msd<K, PAIRS, MsdLocalS>(s, keys, vals, n, stream, src_in, vsrc_in);
-    case 5: return run_msd<K, PAIRS, MsdLocalM>(s, keys, vals, n, stream, src_in, vsrc_in);
-    case 1:
-      if constexpr (sizeof(K) == 8) return run_msd<K, PAIRS, MsdLocalW>(s, keys, vals, n, stream, src_in, vsrc_in);
-      return run_msd<K, PAIRS, MsdLocalA>(s, keys, vals, n, stream, src_in, vsrc_in);
-    case 2: return run_msd<K, PAIRS, MsdLocalB>(s, keys, vals, n, stream, src_in, vsrc_in);
-    case 3:
-      if constexpr (sizeof(K) == 4 && !PAIRS) return run_msd<K, PAIRS, MsdLocalC>(s, keys, vals, n, stream, src_in, vsrc_in);
-      [[fallthrough]];
-    case 6:
-      if constexpr (sizeof(K) == 4 && !PAIRS) return run_msd<K, PAIRS, MsdLocalD>(s, keys, vals, n, stream, src_in, vsrc_in);
-      [[fallthrough]];
-    case 7:
-      if constexpr (sizeof(K) == 4 && !PAIRS) return run_msd<K, PAIRS, MsdLocalC2>(s, keys, vals, n, stream, src_in, vsrc_in);
-      [[fallthrough]];
-    default: return set_err(GRS_EINVAL, "internal: no MSD shape for this n");
-  }
+  // (GRS_OPT_P3_SHAPE pins the shape; everything else in the schedule goes by n)
+  grs_status r = GRS_OK;
+  const bool known = with_msd_shape<K, PAIRS>(msd_shape_code(s->p3_shape, n, sizeof(K) + (PAIRS ? 4 : 0)), [&](auto shape) {
+    r = run_msd<K, PAIRS, decltype(shape)>(s, keys, vals, n, stream, src_in, vsrc_in);
+  });
+  return known ? r : set_err(GRS_EINVAL, "internal: no MSD shape for this n");
 }
 
 // Stable key-range partition with N (compile-time) splitters: one bucket histogram + one pass
@@ -3682,6 +3752,22 @@ grs_status grs_lds_order_check(int device, int blocks, int items, unsigned long 
   if (d) (void)hipFree(d);
   if (prev != device) (void)hipSetDevice(prev);
   return r;
+}
+
+const char* grs_debug_p3_kernel(grs_key_type key_type, int pairs, size_t n, int p3_mode, int p3_shape) {
+  if (n == 0 || n > GRS_MAX_N || p3_mode < 0 || p3_mode > 2) return nullptr;
+  const char* name = nullptr;
+  auto pick = [&](auto key, auto with_payload) {
+    using K = decltype(key);
+    constexpr bool PAIRS = decltype(with_payload)::value;
+    (void)with_msd_shape<K, PAIRS>(msd_shape_code(p3_shape, n, sizeof(K) + (PAIRS ? 4 : 0)), [&](auto shape) {
+      name = msd_p3_kernel_name(msd_p3_kernel<K, PAIRS, decltype(shape)>(n, p3_mode));
+    });
+  };
+  if (key_type == GRS_KEY_U32 && pairs) pick(uint32_t{}, std::true_type{});
+  else if (key_type == GRS_KEY_U32) pick(uint32_t{}, std::false_type{});
+  else if (key_type == GRS_KEY_U64 && !pairs) pick(uint64_t{}, std::false_type{});
+  return name;   // (u64 pairs: the LSD passes)
 }
 
 const char* grs_pass_kernel(const grs_sorter* s, size_t n) {

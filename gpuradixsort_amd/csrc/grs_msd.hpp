@@ -182,7 +182,10 @@ __global__ __launch_bounds__(1024) void grs_seg_plan(const uint32_t* __restrict_
 // grid over the plan's tiles; also zeroes the status words of the first segmented pass
 // (`zero`, rows of `radix` words; the layout is known only from the plan).
 // shift_dev (nullable): digit p is bits [*shift_dev + shift0 + 8p, +8) (a shift found on the device).
-template <typename K, int ND>
+// SOLO: solo segments are counted too -- for a caller that reads the rows itself (the MSD sort's
+// P1 redo: its one segment is the whole input, solo up to one tile of keys, and the plans of P2
+// take the top digit's counts from the row; skipped, they read zeros and the sort moved nothing).
+template <typename K, int ND, bool SOLO = false>
 __global__ __launch_bounds__(256) void grs_seg_hist(const K* __restrict__ keys,
                                                     const SegTile* __restrict__ rec,
                                                     const uint32_t* __restrict__ hdr, int shift0,
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(256) void grs_seg_hist(const K* __restrict__ keys,
     zero[i] = 0;
   for (uint32_t k = blockIdx.x; k < tiles; k += gridDim.x) {
     const SegTile r = rec[k];
-    if ((r.flags >> 8) & 1u) continue;   // solo (uniform: one record per workgroup)
+    if (!SOLO && ((r.flags >> 8) & 1u)) continue;   // solo (uniform: one record per workgroup)
     for (uint32_t i = t; i < ND * 256; i += 256) h[i] = 0;
     __syncthreads();
     // U loads in flight per thread before any is counted (a tile is 17-36K keys: 8-18 each)

@@ -97,6 +97,16 @@ class RadixSorter:
         check(lib().grs_debug_msd_flags(self._h, f), "grs_debug_msd_flags")
         return {"p1_redo": bool(f[0]), "p2_exact": bool(f[1]), "top_shift": int(f[2])}
 
+    def p3_kernel(self, n: int) -> Optional[str]:
+        """Name of the kernel instantiation the MSD schedule's segment sort (P3) launches for a
+        sort() of n items under this sorter's "p3" and "p3_shape" options (grs_debug_p3_kernel;
+        host only), e.g. "grs_msd_local16<512,34>"; None when the MSD schedule has no shape for
+        n items of this type."""
+        kt = GRS_KEY_U32 if self.key_bits == 32 else GRS_KEY_U64
+        name = lib().grs_debug_p3_kernel(kt, int(self.pairs), int(n), self.get_option("p3"),
+                                         self.get_option("p3_shape"))
+        return name.decode() if name else None
+
     @property
     def rank_mode(self) -> str:
         """'atomic' (lane-ordered LDS atomics, the default) or 'match' (ballot fallback)."""

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define GRS_VERSION 410 /* 4.1.0: grs_debug_msd_flags, grs_shard_chunk_plan_host, options
+#define GRS_VERSION 410 /* 4.1.0: grs_debug_msd_flags, grs_debug_p3_kernel, GRS_OPT_P3_SHAPE (test hooks), grs_shard_chunk_plan_host, options
                            GRS_OPT_H2_PIECE, GRS_OPT_P3, GRS_OPT_X_CHUNKS and GRS_OPT_EXCHANGE = 3
                            (additions only).  4.0.0: grs_timing gained `kind` (3.x callers'
                            structs are 4 bytes shorter); guard bands + grs_debug_check_guards;
@@ -125,6 +125,14 @@ grs_status grs_debug_check_guards(grs_sorter* s, uint64_t* bad_words);
  * shift.  Synchronises the device.  New with respect to the reference. */
 grs_status grs_debug_msd_flags(grs_sorter* s, uint32_t flags[3]);
 
+/* TEST HOOK, host only (no device is touched): the kernel instantiation the MSD schedule's
+ * segment sort (P3) launches for a sort of n items of key_type (pairs: with a u32 payload) under
+ * GRS_OPT_P3 = p3_mode and GRS_OPT_P3_SHAPE = p3_shape, e.g. "grs_msd_local<256,8>",
+ * "grs_msd_local16<512,34>", "grs_msd_local_pf<768,24>" -- read from the selection the launch
+ * itself reads.  NULL when the MSD schedule has no shape for that n and type (the LSD passes
+ * sort it).  The string is static.  New with respect to the reference. */
+const char* grs_debug_p3_kernel(grs_key_type key_type, int pairs, size_t n, int p3_mode, int p3_shape);
+
 /* Ranking used by this sorter's passes: 0 = lane-ordered LDS atomics (the default; probed on
  * the device at grs_create), 1 = wave64 ballot-match fallback (probe failed, or
  * grs_set_option(GRS_OPT_RANK, 1)).  -1 for a NULL sorter. */
@@ -204,9 +212,21 @@ typedef enum grs_option {
                                 (default) one workgroup per segment (u32 keys at ~2^30: the low
                                 halves in LDS, three workgroups a CU), 1 persistent workgroups that
                                 load the next segment while storing this one (slower; A/B runs),
-                                2 one workgroup per segment, whole keys in LDS (A/B runs) */
-  GRS_OPT_X_CHUNKS = 16      /* chunks of the chunked exchange (GRS_OPT_EXCHANGE = 3): 0 (default)
+                                2 one workgroup per segment, whole keys in LDS (A/B runs).  Every
+                                instantiation behind these modes is run at small n against the
+                                oracle, its shape pinned by GRS_OPT_P3_SHAPE
+                                (tests/test_gpu_p3_shapes.py) */
+  GRS_OPT_X_CHUNKS = 16,     /* chunks of the chunked exchange (GRS_OPT_EXCHANGE = 3): 0 (default)
                                 4, else 1..16; the same on every rank */
+  GRS_OPT_P3_SHAPE = 17      /* TEST HOOK: the LDS shape of the MSD sort's segment sort (P3), which
+                                a sort chooses from n alone: 0 (default) by size, else the shape
+                                (keys a segment holds): 4 = S 256 x 8, 5 = M 256 x 12, 1 = A
+                                256 x 20 (u64 keys: W 1024 x 5), 2 = B 512 x 20, and for u32 keys
+                                without payload 7 = C2 768 x 23, 3 = C 768 x 24, 6 = D 1024 x 36
+                                (GRS_EINVAL for the other types, which have no such kernel).  The
+                                rest of the schedule (MSD or LSD, tiles, sampled or exact byte-2
+                                scatter) keeps going by n.  The tests run every P3 instantiation
+                                at small n through it; grs_debug_p3_kernel names the kernel */
 } grs_option;
 grs_status grs_set_option(grs_sorter* s, grs_option opt, int value);
 grs_status grs_get_option(const grs_sorter* s, grs_option opt, int* value);

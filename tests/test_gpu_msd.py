@@ -101,11 +101,14 @@ def _segment_keys(rng, sizes):
 
 
 @pytest.mark.parametrize("sizes", [
-    [5120, 5121, 1, 2, 4096],                  # P3 shape A edge (n < 2^26: shape A)
+    [5120, 5121, 1, 2, 4096],                  # past P3's shape here (below ~108M keys: shape S,
+                                               # 2048 keys): the mid list
     [5121] * 7 + [100],                        # solo fallback segments
     [36864, 36865, 73729, 200000, 3],          # one-tile, two-tile and multi-tile fallbacks
     [1 << 20],                                 # one segment of everything
     [6000, 10000, 18432, 18433, 100],          # the mid list (the larger LDS shape) and past it
+    [2047, 2048, 2049, 3, 2048, 1, 2049],      # shape S's own capacity edge (the other shapes'
+                                               # edges: test_gpu_p3_shapes.py)
 ])
 def test_msd_segment_edges(gpu, sizes):
     rng = np.random.default_rng(sum(sizes))
@@ -263,7 +266,9 @@ def test_msd_typed_segment_edges_and_spill(gpu, kb, pairs):
     """The fallback (solo and multi-tile segments) and the region redo for u32 pairs and u64."""
     rng = np.random.default_rng(kb + pairs)
     dt = np.uint32 if kb == 32 else np.uint64
-    sizes = [5120, 5121, 10240, 10241, 17408, 17409, 40000, 3]
+    # shape S runs here (2048 keys; its edge first), the mid list is B's (10240), the fallback's
+    # tile 17408
+    sizes = [2047, 2048, 2049, 5120, 5121, 10240, 10241, 17408, 17409, 40000, 3]
     parts = []
     for i, c in enumerate(sizes):
         prefix = dt((i * 2654435761) & 0xFFFF) << dt(kb - 16)

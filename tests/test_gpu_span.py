@@ -87,6 +87,39 @@ def test_guess_misses_a_varying_bit(gpu, kb, pairs):
     assert np.array_equal(_sort_np(keys2, gpu, pairs)[0], np.sort(keys2))
 
 
+@pytest.mark.parametrize("kb,pairs", [(32, False), (32, True), (64, False)])
+def test_guess_misses_a_varying_bit_in_a_small_sort(gpu, kb, pairs):
+    """The same miss in sorts the redo covers with ONE tile (4096 < n <= 36864 u32 keys, 17408
+    u32 pairs / u64 keys) and with two: the redo's plan is then a solo segment, which the
+    segmented histogram used to skip, so P2's plans read zero counts and the sort returned its
+    input unsorted.  The redo must have run (p1_redo) and the output is the stable sort."""
+    import gpuradixsort_amd as grs
+
+    dt = np.uint32 if kb == 32 else np.uint64
+    tile = 36864 if kb == 32 and not pairs else 17408
+    s = grs.RadixSorter(1 << 20, key_bits=kb, pairs=pairs, radix_bits=8)
+    s.set_option("msd", "always")
+    for n in (4097, 12054, tile, tile + 1, 2 * tile + 1):
+        rng = np.random.default_rng(n + kb + pairs)
+        keys = rng.integers(0, 1 << 20, n).astype(dt)
+        seen = np.zeros(n, bool)
+        seen[_guess_positions(n)] = True
+        keys[rng.choice(np.flatnonzero(~seen), 1)] |= dt(1) << dt(kb - 1)
+        k = torch.from_numpy(keys).to(gpu)
+        v = torch.arange(n, dtype=torch.int32, device=gpu).view(torch.uint32) if pairs else None
+        s.sort(k, v)
+        torch.cuda.synchronize()
+        s.check_error()
+        assert s.check_guards() == 0
+        f = s.msd_flags()
+        assert f["p1_redo"] and f["top_shift"] == kb - 8, (n, f)
+        perm = oracle.stable_argsort(keys)
+        assert np.array_equal(k.cpu().numpy(), keys[perm]), n
+        if pairs:
+            assert np.array_equal(v.cpu().numpy(), perm), n
+    s.close()
+
+
 @pytest.mark.parametrize("name", ["offset_range", "low_16", "low_12", "mid_bits", "two_values",
                                   "top_only", "sparse_high"])
 def test_narrow_spans(gpu, name):
