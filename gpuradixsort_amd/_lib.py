@@ -72,6 +72,7 @@ OPTIONS = {
     "x_chunks": (16, {"default": 0}),
     # test hook: the MSD sort's P3 shape, by size or pinned (W: u64 keys' shape in A's place;
     # C2, C, D: u32 keys without payload only)
+    "p2_half": (18, {"auto": 0, "never": 1}),
     "p3_shape": (17, {"size": 0, "S": 4, "M": 5, "A": 1, "W": 1, "B": 2, "C2": 7, "C": 3, "D": 6}),
 }
 
@@ -85,6 +86,7 @@ SIGNATURES = [
     ("grs_scratch_bytes", c_size_t, [c_void_p]),
     ("grs_debug_check_guards", c_int, [c_void_p, POINTER(c_uint64)]),
     ("grs_debug_msd_flags", c_int, [c_void_p, POINTER(c_uint32)]),
+    ("grs_debug_p2_half_hi", c_uint32, [c_uint32, c_int, c_uint32]),
     ("grs_debug_p3_kernel", c_char_p, [c_int, c_int, c_size_t, c_int, c_int]),
     ("grs_rank_mode", c_int, [c_void_p]),
     ("grs_lds_order_check", c_int, [c_int, c_int, c_int, POINTER(c_ulonglong)]),

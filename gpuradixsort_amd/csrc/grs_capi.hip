@@ -322,6 +322,8 @@ struct grs_sorter {
   int p3_mode = 0;                 // GRS_OPT_P3: 0 a workgroup per segment, 1 persistent with
                                    // prefetch (u32 keys / pairs; measured slower, round 6), 2 as 0
                                    // without the low-halves kernel for C4's size
+  int p2_half = 0;                 // GRS_OPT_P2_HALF: 0 by type and shape (u32 keys whose P3 is
+                                   // grs_msd_local16: P2's regions hold low halves), 1 never
   int seg_route = 0;               // GRS_OPT_SEG_ROUTE: 0 by shape, 1 segmented passes, 2 one
                                    // composite-key sort (grs_sort_segmented's longer segments)
   int msd_mode = -1;               // GRS_OPT_MSD: -1 by size, 0 never, 1 whenever it applies,
@@ -345,6 +347,7 @@ struct grs_sorter {
   int last_msd_cb = -1;            // the control block of the last sort when it ran the MSD
                                    // schedule, else -1 (grs_debug_msd_flags)
   uint32_t* last_msd_spill2 = nullptr;
+  bool last_msd_half = false;      // that sort's P2 was launched storing low halves in its regions
   size_t alt_inner_band = 0;       // u32 pairs: the band between alt's keys and payload, which
   bool alt_band_dirty = false;     // the LSD record passes write records across (restored by
                                    // the next MSD sort or guard check)
@@ -544,7 +547,7 @@ static_assert(BigTile<uint32_t, true>::TILE == kMsdTileMin && BigTile<uint64_t, 
 
 struct MsdLayout {   // word offsets into msd_buf
   size_t h2, h2x, h2s, big, spill2, mid, clear, dstart, reg, room, len2, in2, out2, tab, hdr2, rec2, hdr2r, rec2r,
-      hdrf, recf, bin, bstart, blen, brow, rows, spill, words;
+      hdrf, recf, bin, bstart, blen, brow, bhi, rows, spill, words;
   size_t r2, rf, bl, mr;   // capacities: P2 records, fallback records, big list, histogram rows
   std::vector<size_t> bands;   // byte offsets of the guard bands between the tables
   // nd: digits of the fallback (2 for u32 keys, 6 for u64)
@@ -567,8 +570,9 @@ struct MsdLayout {   // word offsets into msd_buf
       return at;
     };
     // h2 (P2's digit totals) | h2x (exact counts, after a P2 spill) | h2s (sampled counts) |
-    // big counters, P2's spill flag | mid list: the first `clear` words zeroed by the sample kernel
-    L.h2 = take(3 * 65536 + 64 + 2 + 3 * 65536);
+    // big counters, P2's spill flag | mid list (count, -, then (in, out, len, hi) per entry): the
+    // first `clear` words zeroed by the sample kernel
+    L.h2 = take(3 * 65536 + 64 + 2 + 4 * 65536);
     L.h2x = L.h2 + 65536;
     L.h2s = L.h2 + 2 * 65536;
     L.big = L.h2 + 3 * 65536;
@@ -592,6 +596,7 @@ struct MsdLayout {   // word offsets into msd_buf
     L.bstart = take(L.bl);
     L.blen = take(L.bl);
     L.brow = take(L.bl);
+    L.bhi = take(L.bl);   // bits 16..31 of a big-list segment read from P2's half regions
     L.rows = take(L.mr * nd * 256);
     L.spill = take(6 * (L.bl + 1));
     L.words = o;
@@ -804,6 +809,10 @@ grs_status grs_set_option(grs_sorter* s, grs_option opt, int value) {
       if (value < 0 || value > 2) return bad();
       s->p3_mode = value;
       break;
+    case GRS_OPT_P2_HALF:
+      if (value < 0 || value > 1) return bad();
+      s->p2_half = value;
+      break;
     case GRS_OPT_P3_SHAPE: {
       const auto none = [](auto) {};
       const bool ok = value == 0 || (s->key_type == GRS_KEY_U32
@@ -859,6 +868,7 @@ grs_status grs_get_option(const grs_sorter* s, grs_option opt, int* value) {
     case GRS_OPT_H2_PIECE: *value = static_cast<int>(s->h2_piece); break;
     case GRS_OPT_P3: *value = s->p3_mode; break;
     case GRS_OPT_P3_SHAPE: *value = s->p3_shape; break;
+    case GRS_OPT_P2_HALF: *value = s->p2_half; break;
     default: return set_err(GRS_EINVAL, "grs_get_option: unknown option");
   }
   return GRS_OK;
@@ -963,6 +973,7 @@ grs_status grs_debug_msd_flags(grs_sorter* s, uint32_t* flags) {
   grs_status r = GRS_OK;
   const uint32_t* hist = s->last_msd_cb == 0 ? s->ctrl : s->ctrl2;
   uint32_t w[3] = {};
+  const bool half = s->last_msd_half;
   if (hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(&w[0], hist + 512 + 256, 4, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(&w[1], s->last_msd_spill2, 4, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -971,6 +982,7 @@ grs_status grs_debug_msd_flags(grs_sorter* s, uint32_t* flags) {
   flags[0] = w[0] != 0u;
   flags[1] = w[1] != 0u;
   flags[2] = w[2];
+  flags[3] = half && w[1] == 0u;   // (after a spill P3 read the exact pass's whole keys, in place)
   (void)hipSetDevice(prev);
   return r;
 }
@@ -1445,6 +1457,7 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
   if ((r = mark()) != GRS_OK) return r;
   s->last_msd_cb = s->cb_i;
   s->last_msd_spill2 = mb + L.spill2;
+  s->last_msd_half = false;
   if (s->cb_dirty && s->cb_i == 0) GRS_HIP(hipMemsetAsync(hist, 0, GRS_CTRL_ERROR * 4, stream));
   s->cb_dirty = false;
   if (s->alt_band_dirty) {   // an LSD record sort wrote across alt's inner guard band: restore it
@@ -1548,18 +1561,34 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
   // sorts): alt -> the region buffer, each 16-bit segment in its region, its first tile writing
   // the region starts (dstart) and its last the totals (h2) and the spill flag; after a spill
   // (or for small sorts, always) the exact pass alt -> keys from H2's exact counts (h2x).
+  // u32 keys whose P3 is grs_msd_local16 (it keeps only the low halves anyway): the sampled
+  // regions hold the low halves only (2 B a key written here and read there instead of 4; the
+  // exact redo after a spill writes whole keys in place as ever).  GRS_OPT_P2_HALF = 1: whole keys
+  const MsdP3Kernel pk = msd_p3_kernel<K, PAIRS, P3C>(n, s->p3_mode);   // (grs_debug_p3_kernel names it)
+  const bool half = sizeof(K) == 4 && !PAIRS && shift != 0 && pk.family == MsdP3Kernel::kLocal16 && s->p2_half == 0;
+  s->last_msd_half = half;
   {
     const Dig d2{-8, 255u};   // the byte below the top digit (+ *top)
     const dim3 grid(static_cast<uint32_t>(t2));
-    constexpr uint32_t RG = 131072;
+    constexpr uint32_t RG = 131072, HALF = 524288;
     auto go = [&](auto tshape) -> grs_status {
       using T = decltype(tshape);
       if (shift) {
         GRS_DIAG_CHECK("plans");
         GRS_DIAG_SET(cap2, region_len);
-        hipLaunchKernelGGL((grs::grs_onesweep_seg<K, PAIRS, 8, T::BLOCK, T::ITEMS, T::MINW, T::OPT | RG, false>),
-                           grid, dim3(T::BLOCK), 0, stream, alt, rk, valt, rv, d2, rec2r, hdr2r, reg, 256u,
-                           tickets + GRS_XCDS, st[1], st[0], err, dstart, h2, spill2, (const uint32_t*)nullptr, top);
+        bool launched_half = false;
+        if constexpr (sizeof(K) == 4 && !PAIRS) {
+          if (half) {
+            hipLaunchKernelGGL((grs::grs_onesweep_seg<K, PAIRS, 8, T::BLOCK, T::ITEMS, T::MINW, T::OPT | RG | HALF, false>),
+                               grid, dim3(T::BLOCK), 0, stream, alt, rk, valt, rv, d2, rec2r, hdr2r, reg, 256u,
+                               tickets + GRS_XCDS, st[1], st[0], err, dstart, h2, spill2, (const uint32_t*)nullptr, top);
+            launched_half = true;
+          }
+        }
+        if (!launched_half)
+          hipLaunchKernelGGL((grs::grs_onesweep_seg<K, PAIRS, 8, T::BLOCK, T::ITEMS, T::MINW, T::OPT | RG, false>),
+                             grid, dim3(T::BLOCK), 0, stream, alt, rk, valt, rv, d2, rec2r, hdr2r, reg, 256u,
+                             tickets + GRS_XCDS, st[1], st[0], err, dstart, h2, spill2, (const uint32_t*)nullptr, top);
         GRS_HIP(hipGetLastError());
         GRS_DIAG_CHECK("P2region");
         GRS_DIAG_SET(n, region_len);
@@ -1596,8 +1625,9 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
   // range after the multi-GPU exchange), beyond that for the fallback (moved to their place
   // first: grs_msd_copy_big)
   using P3L = std::conditional_t<sizeof(K) == 4 && !PAIRS, MsdLocalC, MsdLocalB>;
-  const MsdP3Kernel pk = msd_p3_kernel<K, PAIRS, P3C>(n, s->p3_mode);   // (grs_debug_p3_kernel names it)
   const uint32_t mid_max = pk.mid_max;
+  const uint32_t* const span_or = half ? span : nullptr;       // (non-null: the regions hold halves)
+  uint32_t* const bhi = half ? mb + L.bhi : nullptr;
   bool launched = false;
   if constexpr (sizeof(K) == 4) {
     if (pk.family == MsdP3Kernel::kLocalPf) {
@@ -1619,12 +1649,14 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
     } else if (pk.family == MsdP3Kernel::kLocal16 && pk.block == 512) {
       hipLaunchKernelGGL((grs::grs_msd_local16<512, 34, 6, FT::TILE>), dim3(65536), dim3(512), 0, stream,
                          (uint32_t*)keys, vals, (const uint32_t*)rk, rv, spill2, mb + L.len2, mb + L.in2, mb + L.out2,
-                         mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top);
+                         mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top,
+                         span_or, bhi);
       launched = true;
     } else if (pk.family == MsdP3Kernel::kLocal16) {
       hipLaunchKernelGGL((grs::grs_msd_local16<1024, 34, 8, FT::TILE>), dim3(65536), dim3(1024), 0, stream,
                          (uint32_t*)keys, vals, (const uint32_t*)rk, rv, spill2, mb + L.len2, mb + L.in2, mb + L.out2,
-                         mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top);
+                         mid_max, mb + L.mid, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, mb + L.brow, rows, top,
+                         span_or, bhi);
       launched = true;
     }
   }
@@ -1642,11 +1674,11 @@ grs_status run_msd(grs_sorter* s, K* keys, uint32_t* vals, uint32_t n, hipStream
     hipLaunchKernelGGL((grs::grs_msd_local_list<K, PAIRS, P3L::BLOCK, P3L::I, P3L::C16, minw>),
                        dim3(per_cu * s->cus), dim3(P3L::BLOCK), 0, stream, keys, vals, rk, rv, spill2, mb + L.mid,
                        top, (const uint32_t*)bigc, (const uint32_t*)(mb + L.bin), (const uint32_t*)(mb + L.bstart),
-                       (const uint32_t*)(mb + L.blen));
+                       (const uint32_t*)(mb + L.blen), (const uint32_t*)bhi);
     GRS_HIP(hipGetLastError());
   } else {
     hipLaunchKernelGGL((grs::grs_msd_copy_big<K, PAIRS>), dim3(4 * s->cus), dim3(256), 0, stream, rk, rv, keys, vals,
-                       spill2, bigc, mb + L.bin, mb + L.bstart, mb + L.blen);
+                       spill2, bigc, mb + L.bin, mb + L.bstart, mb + L.blen, (const uint32_t*)bhi);
     GRS_HIP(hipGetLastError());
   }
   GRS_DIAG_CHECK("P3");
@@ -3768,6 +3800,11 @@ const char* grs_debug_p3_kernel(grs_key_type key_type, int pairs, size_t n, int 
   else if (key_type == GRS_KEY_U32) pick(uint32_t{}, std::false_type{});
   else if (key_type == GRS_KEY_U64 && !pairs) pick(uint64_t{}, std::false_type{});
   return name;   // (u64 pairs: the LSD passes)
+}
+
+uint32_t grs_debug_p2_half_hi(uint32_t or_keys, int top_shift, uint32_t segment) {
+  if (top_shift < 8 || top_shift > 24 || segment > 0xFFFFu) return 0xFFFFFFFFu;
+  return grs::msd_half_hi(or_keys, static_cast<uint32_t>(top_shift), segment);
 }
 
 const char* grs_pass_kernel(const grs_sorter* s, size_t n) {

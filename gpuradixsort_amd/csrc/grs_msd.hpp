@@ -267,6 +267,14 @@ __device__ __forceinline__ K span_join(uint32_t lo, uint32_t hi) {
   if constexpr (sizeof(K) == 8) return (static_cast<K>(hi) << 32) | lo;
   else return static_cast<K>(lo);
 }
+// Bits 16..31 of every key of 16-bit segment b = bucket * 256 + digit2 of u32 keys, for top shift
+// s in [8, 24] and or_keys = the OR of all keys (span word 0): b holds key bits [s - 8, s + 8), and
+// the bits from s + 8 up are the same in every key (msd_top_shift), so they are the OR's.  P2
+// keeps only the low halves in its regions (grs_pass.hpp OPT 524288); P3 widens them with this.
+__host__ __device__ inline uint32_t msd_half_hi(uint32_t or_keys, uint32_t s, uint32_t b) {
+  const uint32_t low_mask = s + 8 >= 32 ? 0xFFFFFFFFu : (1u << (s + 8)) - 1u;
+  return ((or_keys & ~low_mask) | (b << (s - 8))) & 0xFFFF0000u;
+}
 // LDS rounds of P3 for top shift s: the bits below the 16-bit segment prefix, [0, s - 8)
 template <int RMAX>
 __device__ __forceinline__ int msd_p3_rounds(uint32_t s) {
@@ -705,7 +713,8 @@ __global__ __launch_bounds__(256) void grs_msd_starts(const uint32_t* __restrict
 // The big-list segments of P3 (longer than any LDS shape) from the region buffer into the
 // caller's arrays at their sorted place, for the in-place fallback (persistent grid, every
 // block on every entry; leaves at once without entries or after a spill, whose exact pass
-// already wrote the caller's arrays).
+// already wrote the caller's arrays).  big_hi (nullable): the regions hold low halves, entry e's
+// keys are big_hi[e] | its halves.
 template <typename K, bool PAIRS>
 __global__ __launch_bounds__(256) void grs_msd_copy_big(const K* __restrict__ rk, const uint32_t* __restrict__ rv,
                                                         K* __restrict__ keys, uint32_t* __restrict__ vals,
@@ -713,11 +722,20 @@ __global__ __launch_bounds__(256) void grs_msd_copy_big(const K* __restrict__ rk
                                                         const uint32_t* __restrict__ big,
                                                         const uint32_t* __restrict__ big_in,
                                                         const uint32_t* __restrict__ big_out,
-                                                        const uint32_t* __restrict__ big_len) {
+                                                        const uint32_t* __restrict__ big_len,
+                                                        const uint32_t* __restrict__ big_hi = nullptr) {
   if (*spill != 0u) return;
   const uint32_t count = big[0];
   for (uint32_t e = 0; e < count; ++e) {
     const uint32_t a = big_in[e], o = big_out[e], n = big_len[e];
+    if constexpr (sizeof(K) == 4 && !PAIRS) {
+      if (big_hi != nullptr) {
+        const uint32_t hi = big_hi[e];
+        const uint16_t* const rh = reinterpret_cast<const uint16_t*>(rk);
+        for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) keys[o + i] = hi | rh[a + i];
+        continue;
+      }
+    }
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
       keys[o + i] = rk[a + i];
       if constexpr (PAIRS) vals[o + i] = rv[a + i];
@@ -806,6 +824,16 @@ struct LocalSort {
       const uint32_t i = w * GRS_WAVE * I + j * GRS_WAVE + lane;
       k[j] = i < len ? kin[lo + i] : K(0);
       if constexpr (PAIRS) v[j] = i < len ? vin[lo + i] : 0u;
+    }
+  }
+  // load() of u32 keys from their low halves (the MSD sort's half regions): key = hi | half
+  __device__ __forceinline__ static void load_half(K (&k)[I], const uint16_t* hin, uint32_t len, uint32_t hi) {
+    static_assert(sizeof(K) == 4 && !PAIRS, "low halves: u32 keys without payload");
+    const uint32_t lane = threadIdx.x & (GRS_WAVE - 1), w = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t j = 0; j < I; ++j) {
+      const uint32_t i = w * GRS_WAVE * I + j * GRS_WAVE + lane;
+      k[j] = i < len ? hi | hin[i] : K(0);
     }
   }
   // `rounds` stable 8-bit rounds from the registers; the sorted segment is left in sm.sk / sm.sv,
@@ -1029,23 +1057,28 @@ struct LocalSort16 {
   }
   // kin[0, len) -> kout[0, len) sorted by bits 0 .. 8 * rounds (rounds 0: the load + store
   // skeleton of the lab, LDS left unwritten).  The slots past len skip the ranking (lanes of one
-  // digit would serialise on its counter) and scatter to their own index, past the keys
-  __device__ __forceinline__ static void run(Smem& sm, const uint32_t* kin, uint32_t* kout, uint32_t len,
-                                             int rounds) {
+  // digit would serialise on its counter) and scatter to their own index, past the keys.
+  // kin: the segment's whole keys (esz 4; hi = their common bits 16..31, read from the first), or
+  // its packed low halves (esz 2, the half regions of P2; hi from the caller: msd_half_hi).  esz
+  // is wave-uniform.
+  __device__ __forceinline__ static void run(Smem& sm, const void* kin, uint32_t esz, uint32_t hi, uint32_t* kout,
+                                             uint32_t len, int rounds) {
     const uint32_t t = threadIdx.x, lane = t & (GRS_WAVE - 1), w = t >> 6;
-    const uint32_t hi = __builtin_amdgcn_readfirstlane(kin[0]) & 0xFFFF0000u;
-    // the low halves only (2-B buffer loads of the same lines: unpredicated, the descriptor's
-    // range check drops the slots past len, one offset register for all I), packed two a register
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(kin), 0, static_cast<int>(4u * len),
+    if (esz == 4u) hi = __builtin_amdgcn_readfirstlane(*static_cast<const uint32_t*>(kin)) & 0xFFFF0000u;
+    // the low halves only (2-B buffer loads at a stride of esz bytes: unpredicated, the
+    // descriptor's range check drops the slots past len, one offset register for all I), packed
+    // two a register
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(kin), 0, static_cast<int>(esz * len),
                                                         0x00020000);
     // (wave-uniform bases: the per-item parts of offsets and bounds stay scalar)
     const uint32_t ws = __builtin_amdgcn_readfirstlane(w), wbase = ws * GRS_WAVE * I;
     const uint32_t wlen = len > wbase ? len - wbase : 0u;   // this wave's slots holding keys
+    const uint32_t voff = esz * lane;
     uint32_t kp[IP];
 #pragma unroll
     for (uint32_t j = 0; j < IP; ++j) {
-      const uint32_t a = __builtin_amdgcn_raw_buffer_load_b16(rsrc, 4u * lane, 4u * (wbase + 2u * j * GRS_WAVE), 0);
-      const uint32_t b = __builtin_amdgcn_raw_buffer_load_b16(rsrc, 4u * lane, 4u * (wbase + (2u * j + 1u) * GRS_WAVE), 0);
+      const uint32_t a = __builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, esz * (wbase + 2u * j * GRS_WAVE), 0);
+      const uint32_t b = __builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, esz * (wbase + (2u * j + 1u) * GRS_WAVE), 0);
       kp[j] = (a & 0xFFFFu) | (b << 16);
     }
     const uint32_t ak = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(kout) / 4u) % 4u;
@@ -1134,29 +1167,37 @@ struct LocalSort16 {
 // in2[b] of the region buffer (rk / rv) -- or, after a P2 spill, of the caller's arrays, in
 // place -- sorted in LDS (LocalSort) and written to out2[b] of the caller's arrays
 // (grs_msd_starts).  Longer segments are listed: up to MID keys in the mid list (mid[0] =
-// count, (in, out, len) from mid[2] on) for grs_msd_local_list's larger shape, longer ones in
+// count, (in, out, len, hi) from mid[2] on) for grs_msd_local_list's larger shape, longer ones in
 // the big list for the segmented LSD in place (grs_msd_copy_big moves them first): big[0] counts
 // them, big[1] counts those longer than one fallback tile (TILEF keys), which get a histogram
 // row (ND digits) zeroed here; big_in / big_start / big_len / big_row hold (region start,
 // sorted start, length, row) per entry.
 // A P3 segment that is not sorted in this shape's LDS: one key (copied to its place, unless in
 // place), or longer than SMAX -- listed: up to mid_max keys in the mid list (mid[0] = count,
-// (in, out, len) from mid[2] on) for grs_msd_local_list's larger shape, longer ones in the big
+// (in, out, len, hi) from mid[2] on) for grs_msd_local_list's larger shape, longer ones in the big
 // list for the segmented LSD in place (grs_msd_copy_big moves them first): big[0] counts them,
 // big[1] counts those longer than one fallback tile (TILEF keys), which get a histogram row (ND
 // digits) zeroed here; big_in / big_start / big_len / big_row hold (region start, sorted start,
 // length, row) per entry.  Uniform in the workgroup; slot: an LDS word.
+// half (u32 keys without payload, not in place): kin holds the low halves only (P2's half
+// regions) and hi the segment's bits 16..31 (msd_half_hi); the lists carry hi (a mid entry's
+// fourth word, big_hi per big entry) for the kernels that read the listed segments.
 template <typename K, bool PAIRS, int BLOCK, uint32_t SMAX, uint32_t ND, uint32_t TILEF>
 __device__ __forceinline__ void msd_local_other(uint32_t len, uint32_t lo, uint32_t o, bool inplace, const K* kin,
                                                 const uint32_t* vin, K* keys, uint32_t* vals, uint32_t mid_max,
                                                 uint32_t* mid, uint32_t* big, uint32_t* big_in,
                                                 uint32_t* big_start, uint32_t* big_len, uint32_t* big_row,
-                                                uint32_t* rows, uint32_t& slot) {
+                                                uint32_t* rows, uint32_t& slot, bool half = false, uint32_t hi = 0,
+                                                uint32_t* big_hi = nullptr) {
   const uint32_t t = threadIdx.x;
   if (len == 1u) {
     if (!inplace && t == 0) {
-      keys[o] = kin[lo];
-      if constexpr (PAIRS) vals[o] = vin[lo];
+      if constexpr (sizeof(K) == 4 && !PAIRS) {
+        keys[o] = half ? hi | reinterpret_cast<const uint16_t*>(kin)[lo] : kin[lo];
+      } else {
+        keys[o] = kin[lo];
+        if constexpr (PAIRS) vals[o] = vin[lo];
+      }
     }
     return;
   }
@@ -1164,15 +1205,17 @@ __device__ __forceinline__ void msd_local_other(uint32_t len, uint32_t lo, uint3
   if (len <= mid_max) {   // the mid list (a larger LDS shape)
     if (t == 0) {
       const uint32_t e = atomicAdd(&mid[0], 1u);
-      mid[2 + 3 * e] = lo;
-      mid[3 + 3 * e] = o;
-      mid[4 + 3 * e] = len;
+      mid[2 + 4 * e] = lo;
+      mid[3 + 4 * e] = o;
+      mid[4 + 4 * e] = len;
+      mid[5 + 4 * e] = hi;
     }
     return;
   }
   if (t == 0) {
     const uint32_t e = atomicAdd(&big[0], 1u);
     const uint32_t row = len > TILEF ? atomicAdd(&big[1], 1u) : 0xFFFFFFFFu;
+    if (big_hi != nullptr) big_hi[e] = hi;
     big_in[e] = lo;
     big_start[e] = o;
     big_len[e] = len;
@@ -1227,7 +1270,8 @@ __global__ __launch_bounds__(BLOCK) void grs_msd_local(K* __restrict__ keys, uin
 
 // P3 of u32 keys without payload on LocalSort16 (the low halves in LDS; three 512 x 34
 // workgroups a CU at 2^30 keys instead of LocalSort's two 768 x 23): grs_msd_local's tables,
-// lists and results.
+// lists and results.  span_or / big_hi (non-null together): P2 stored only the low halves in
+// its regions (grs_pass.hpp OPT 524288), read here packed unless it spilled.
 template <int BLOCK, int I, int MINW, uint32_t TILEF>
 __global__ __launch_bounds__(BLOCK, MINW) void grs_msd_local16(
     uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, const uint32_t* __restrict__ rk,
@@ -1235,7 +1279,8 @@ __global__ __launch_bounds__(BLOCK, MINW) void grs_msd_local16(
     const uint32_t* __restrict__ in2, const uint32_t* __restrict__ out2, uint32_t mid_max, uint32_t* __restrict__ mid,
     uint32_t* __restrict__ big, uint32_t* __restrict__ big_in, uint32_t* __restrict__ big_start,
     uint32_t* __restrict__ big_len, uint32_t* __restrict__ big_row, uint32_t* __restrict__ rows,
-    const uint32_t* __restrict__ top_shift) {
+    const uint32_t* __restrict__ top_shift, const uint32_t* __restrict__ span_or = nullptr,
+    uint32_t* __restrict__ big_hi = nullptr) {
   using LS = LocalSort16<BLOCK, I>;
   __shared__ typename LS::Smem sm;
   const uint32_t len = len2[blockIdx.x];
@@ -1243,13 +1288,20 @@ __global__ __launch_bounds__(BLOCK, MINW) void grs_msd_local16(
   const bool inplace = __builtin_amdgcn_readfirstlane(*spill) != 0u;
   const uint32_t lo = in2[blockIdx.x], o = out2[blockIdx.x];
   const uint32_t* const kin = inplace ? keys : rk;
+  const uint32_t top = __builtin_amdgcn_readfirstlane(*top_shift);
+  // span_or (nullable, the OR of the keys): P2 left low halves in the regions (read unless it
+  // spilled); the segment's high half from its index, no key read for it
+  const bool half = span_or != nullptr && !inplace;
+  const uint32_t hi = half ? msd_half_hi(__builtin_amdgcn_readfirstlane(*span_or), top, blockIdx.x) : 0u;
   if (len == 1u || len > LS::SMAX) {
     msd_local_other<uint32_t, false, BLOCK, LS::SMAX, 2, TILEF>(len, lo, o, inplace, kin, nullptr, keys, vals, mid_max,
                                                                 mid, big, big_in, big_start, big_len, big_row, rows,
-                                                                sm.slot);
+                                                                sm.slot, half, hi, big_hi);
     return;
   }
-  LS::run(sm, kin + lo, keys + o, len, msd_p3_rounds<2>(__builtin_amdgcn_readfirstlane(*top_shift)));
+  const void* const src = half ? static_cast<const void*>(reinterpret_cast<const uint16_t*>(kin) + lo)
+                               : static_cast<const void*>(kin + lo);
+  LS::run(sm, src, half ? 2u : 4u, hi, keys + o, len, msd_p3_rounds<2>(top));
 }
 
 // P3 persistent (keys sorted in at most two LDS rounds: u32 keys, u32 pairs): grid = resident
@@ -1333,16 +1385,29 @@ __global__ __launch_bounds__(BLOCK, MINW) void grs_msd_local_list(K* __restrict_
                                                             const uint32_t* __restrict__ big = nullptr,
                                                             const uint32_t* __restrict__ big_in = nullptr,
                                                             const uint32_t* __restrict__ big_out = nullptr,
-                                                            const uint32_t* __restrict__ big_len = nullptr) {
+                                                            const uint32_t* __restrict__ big_len = nullptr,
+                                                            const uint32_t* __restrict__ big_hi = nullptr) {
   using LS = LocalSort<K, PAIRS, BLOCK, I, C16>;
   __shared__ typename LS::Smem sm;
   const bool inplace = *spill != 0u;
+  // big_hi (nullable, u32 keys without payload): the regions hold low halves (unless P2 spilled);
+  // a listed segment's keys are its hi (big_hi[e], a mid entry's fourth word) | its halves
+  bool half = false;
+  if constexpr (sizeof(K) == 4 && !PAIRS) half = big_hi != nullptr && !inplace;
+  const uint16_t* const rh = reinterpret_cast<const uint16_t*>(rk);
   // big (nullable): grs_msd_copy_big's work first, so that it needs no launch of its own (every
   // workgroup takes a slice of every entry; disjoint from the mid list's segments)
   if (big != nullptr && !inplace) {
     const uint32_t nb = big[0];
     for (uint32_t e = 0; e < nb; ++e) {
       const uint32_t a = big_in[e], o = big_out[e], n = big_len[e];
+      if constexpr (sizeof(K) == 4 && !PAIRS) {
+        if (half) {
+          const uint32_t hi = big_hi[e];
+          for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) keys[o + i] = hi | rh[a + i];
+          continue;
+        }
+      }
       for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         keys[o + i] = rk[a + i];
         if constexpr (PAIRS) vals[o + i] = rv[a + i];
@@ -1355,7 +1420,18 @@ __global__ __launch_bounds__(BLOCK, MINW) void grs_msd_local_list(K* __restrict_
   const uint32_t* const vin = inplace ? vals : rv;
   const int rounds = msd_p3_rounds<LS::ROUNDS>(__builtin_amdgcn_readfirstlane(*top_shift));
   for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
-    const uint32_t lo = mid[2 + 3 * e], o = mid[3 + 3 * e], len = mid[4 + 3 * e];
+    const uint32_t lo = mid[2 + 4 * e], o = mid[3 + 4 * e], len = mid[4 + 4 * e];
+    if constexpr (sizeof(K) == 4 && !PAIRS) {
+      if (half) {   // run_vec from the half source (u32 keys: at most two rounds)
+        K k[I];
+        typename LS::Vals v;
+        LS::load_half(k, rh + lo, len, mid[5 + 4 * e]);
+        LS::sort_rounds(sm, k, v, len, rounds, LS::template mis<K, LS::KV>(keys + o), 0u);
+        LS::template copy_out<K, LS::KV>(keys + o, sm.sk, len);
+        __syncthreads();
+        continue;
+      }
+    }
     LS::template run_vec<>(sm, kin + lo, PAIRS ? vin + lo : nullptr, keys + o, PAIRS ? vals + o : nullptr,
                            len, rounds);
     __syncthreads();   // every LDS read of this segment before the next one's

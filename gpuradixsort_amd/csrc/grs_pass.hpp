@@ -253,6 +253,10 @@ using V4SmemFor = V4Smem<K, PAIRS, RB, BLOCK, ITEMS, (OPT & 256) != 0, DigitF::k
 //        4n-byte arrays hold n records that way)
 //   262144 span: the ranking also ORs the tile's valid keys and their complements into sm.span
 //        (zeroed by the kernel; the MSD sort's first scatter learns the keys' exact bit span)
+//   524288 low halves: a region pass of u32 keys without payload stores only bits 0..15 of
+//        each key, at the same element index of keys_out viewed as uint16_t (the MSD sort's P2
+//        when P3 is grs_msd_local16: every key of a 16-bit segment agrees in bits 16..31, which
+//        P3 rebuilds from the segment's index, grs_msd.hpp msd_half_hi)
 
 // Load tile `tile` wave-striped: item j of lane l of wave w is tile key w*64*ITEMS + j*64 + l.
 // Keys past n (last tile) are all-ones padding, which sorts after every valid key of its digit.
@@ -639,6 +643,9 @@ __device__ __forceinline__ uint32_t onesweep_tile(
       } else {
         reinterpret_cast<unsigned long long*>(keys_out)[dst] = x;
       }
+    } else if constexpr ((OPT & 524288) != 0) {
+      static_assert(sizeof(K) == 4 && !PAIRS && (OPT & 131072) != 0, "low halves: u32 keys, a region pass");
+      reinterpret_cast<uint16_t*>(keys_out)[dst] = static_cast<uint16_t>(kk);
     } else {
       keys_out[dst] = kk;
       if constexpr (PAIRS) vals_out[dst] = sm.vals[i];

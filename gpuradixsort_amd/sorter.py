@@ -89,13 +89,17 @@ class RadixSorter:
         check(lib().grs_debug_check_guards(self._h, ctypes.byref(bad)), "grs_debug_check_guards")
         return int(bad.value)
 
-    def msd_flags(self) -> dict:
+    def msd_flags(self, p2_half: bool = False) -> dict:
         """What the last sort did in the MSD schedule (grs_debug_msd_flags; synchronises):
         p1_redo (P1 ran twice), p2_exact (P2 took the exact path), top_shift (the top digit's
-        shift).  GrsError when the last sort took the LSD passes."""
-        f = (ctypes.c_uint32 * 3)()
+        shift) and, when asked for with p2_half=True, p2_half (P3 read low halves from P2's
+        regions, option "p2_half").  GrsError when the last sort took the LSD passes."""
+        f = (ctypes.c_uint32 * 4)()
         check(lib().grs_debug_msd_flags(self._h, f), "grs_debug_msd_flags")
-        return {"p1_redo": bool(f[0]), "p2_exact": bool(f[1]), "top_shift": int(f[2])}
+        flags = {"p1_redo": bool(f[0]), "p2_exact": bool(f[1]), "top_shift": int(f[2])}
+        if p2_half:
+            flags["p2_half"] = bool(f[3])
+        return flags
 
     def p3_kernel(self, n: int) -> Optional[str]:
         """Name of the kernel instantiation the MSD schedule's segment sort (P3) launches for a

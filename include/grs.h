@@ -106,6 +106,9 @@ void grs_destroy(grs_sorter* s);
  *     the second buffer grows to 1.125 n + 1M elements and a region buffer of 1.3 n + 4M
  *     elements joins it, ~2.45 n E in all (C4's 2^30 u32 keys: ~10.5 GB beside its 4.3 GB of
  *     keys); grs_set_option(GRS_OPT_MSD, 0) releases it (the sorter then runs the LSD passes).
+ *     The region buffer keeps that size where the sort writes only the low halves of u32 keys
+ *     into it (GRS_OPT_P2_HALF: its first half is used then; a spill's exact redo and the other
+ *     P3 shapes still need whole elements).
  * If the MSD scratch does not fit at grs_create, the sorter is created without it. */
 size_t grs_scratch_bytes(const grs_sorter* s);
 
@@ -122,8 +125,16 @@ grs_status grs_debug_check_guards(grs_sorter* s, uint64_t* bad_words);
  * took the LSD passes): flags[0] = 1 when P1 ran twice (a run outgrew its sampled region, or the
  * keys' span put the top digit above the sample's guess), flags[1] = 1 when P2 took the exact
  * path (a sampled region overflowed, or a sort too small to sample), flags[2] = the top digit's
- * shift.  Synchronises the device.  New with respect to the reference. */
-grs_status grs_debug_msd_flags(grs_sorter* s, uint32_t flags[3]);
+ * shift, flags[3] = 1 when P3 read low halves from P2's sampled regions (GRS_OPT_P2_HALF; 0 after
+ * a spill, whose exact pass wrote whole keys in place).  Synchronises the device.  New with
+ * respect to the reference. */
+grs_status grs_debug_msd_flags(grs_sorter* s, uint32_t flags[4]);
+
+/* TEST HOOK, host only: bits 16..31 that the MSD sort's P3 gives the keys of 16-bit segment
+ * `segment` (top-digit bucket * 256 + second digit, < 65536) when P2's regions hold only low
+ * halves of u32 keys: or_keys = the OR of all keys, top_shift = the top digit's shift (8..24).  The
+ * function the kernels call (grs_msd.hpp msd_half_hi); 0xFFFFFFFF for arguments out of range. */
+uint32_t grs_debug_p2_half_hi(uint32_t or_keys, int top_shift, uint32_t segment);
 
 /* TEST HOOK, host only (no device is touched): the kernel instantiation the MSD schedule's
  * segment sort (P3) launches for a sort of n items of key_type (pairs: with a u32 payload) under
@@ -218,6 +229,13 @@ typedef enum grs_option {
                                 (tests/test_gpu_p3_shapes.py) */
   GRS_OPT_X_CHUNKS = 16,     /* chunks of the chunked exchange (GRS_OPT_EXCHANGE = 3): 0 (default)
                                 4, else 1..16; the same on every rank */
+  GRS_OPT_P2_HALF = 18,      /* the MSD sort of u32 keys without payload from 2^26 keys, where P3 is
+                                the low-halves kernel (grs_msd_local16: ~2^30 keys and past 1.13G):
+                                0 (default) P2 writes only bits 0..15 of each key into its sampled
+                                regions (every key of a 16-bit segment agrees above them; P3
+                                rebuilds them from the segment's index): 2 B a key written and
+                                read there instead of 4; 1 whole keys in the regions (A/B runs).
+                                Other types, sizes and P3 kernels always keep whole keys */
   GRS_OPT_P3_SHAPE = 17      /* TEST HOOK: the LDS shape of the MSD sort's segment sort (P3), which
                                 a sort chooses from n alone: 0 (default) by size, else the shape
                                 (keys a segment holds): 4 = S 256 x 8, 5 = M 256 x 12, 1 = A
